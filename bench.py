@@ -5,14 +5,20 @@ BASELINE.json config #2 ("MulticlassConfusionMatrix num_classes=1000, batch=8192
 Metric: metric-updates/sec summed over the node (each rank updates its own metric on its own 8192-row batches;
 weak scaling: per-GPU work is fixed).  The timed region of one run is K ``update`` calls followed by one synced
 ``compute()`` (RCCL all-reduce of the 1000x1000 int64 state), bracketed by barrier + ``torch.cuda.synchronize()``;
-the max over ranks is reported.  ``compute_ms`` (sync + compute wall-clock) is measured separately.
+the max over ranks is reported.
 
-The same loop is also run through an op-for-op emulation of the reference implementation (``benchmarks/reference_path.py``)
-on the same data in the same process; ``vs_baseline`` = ours / emulated reference.
+A plain run does only that: set up, W warm-up updates, the K timed steps, one JSON result line.  ``--full`` adds what
+takes runs of its own: ``compute_ms`` (sync + compute wall-clock, measured separately over 5 repetitions) and the same
+loop run through an op-for-op emulation of the reference implementation (``benchmarks/reference_path.py``) on the same
+data in the same process, parity-checked; ``vs_baseline`` = ours / emulated reference (``--no-baseline`` skips it).
 
-Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W]``.  ``--gpus N`` always means N ranks: under a launcher
-(``torch.distributed.run``, ``WORLD_SIZE`` set) the world size must equal N or the run exits non-zero; without one,
-N > 1 spawns ``torch.distributed.run --nproc-per-node N`` itself as a child process before any GPU call
+``--dump-outputs DIR`` writes what the timed region returned to its caller, the synced ``compute()`` result after the
+K-th update, as ``DIR/confmat.npy`` (float64, exact for these counts).  The inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
+
+Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]``.
+``--gpus N`` always means N ranks: under a launcher (``torch.distributed.run``, ``WORLD_SIZE`` set) the world size
+must equal N or the run exits non-zero; without one, N > 1 spawns ``torch.distributed.run --nproc-per-node N`` itself as a child process before any GPU call
 (``benchmarks/_dist.py`` ``launch``).
 """
 import argparse
@@ -91,9 +97,9 @@ def _warm(metric, preds, target, warmup: int) -> None:
     _reset(metric)
 
 
-def _timed(metric, preds, target, steps: int, warmup: int, device, world):
-    """EXACTLY ``steps`` updates and one synced compute(), bracketed by barrier + synchronize; then the synced
-    compute() wall-clock on its own (5 reps)."""
+def _timed(metric, preds, target, steps: int, warmup: int, device, world, full: bool):
+    """EXACTLY ``steps`` updates and one synced compute(), bracketed by barrier + synchronize; with ``full``, then the
+    synced compute() wall-clock on its own (5 reps)."""
     nbuf = len(preds)
     _barrier_sync(device, world)
     t0 = time.perf_counter()
@@ -108,6 +114,8 @@ def _timed(metric, preds, target, steps: int, warmup: int, device, world):
     # host-side phases of the timed region: issuing the K updates, compute() (sync + validation read: it waits for the
     # device to drain), the closing barrier + synchronize
     phases = {"update_issue_ms": (t1 - t0) * 1e3, "compute_ms": (t2 - t1) * 1e3, "closing_sync_ms": (t3 - t2) * 1e3}
+    if not full:
+        return elapsed, None, result, phases
     # separate measurement of the synced compute wall-clock
     _barrier_sync(device, world)
     c0 = time.perf_counter()
@@ -115,7 +123,7 @@ def _timed(metric, preds, target, steps: int, warmup: int, device, world):
     for _ in range(reps):
         if hasattr(metric, "_computed"):
             metric._computed = None
-        result = metric.compute()
+        metric.compute()
     _barrier_sync(device, world)
     compute_ms = (time.perf_counter() - c0) / reps * 1e3
     return elapsed, compute_ms, result, phases
@@ -128,12 +136,26 @@ def _reset(metric) -> None:
         metric.confmat.zero_()
 
 
+def _dump_outputs(out_dir: str, result: torch.Tensor) -> None:
+    """The timed region's return value, the synced [C, C] confusion matrix (identical on every rank), as
+    ``confmat.npy`` in float64: counts stay far below 2**53, so the conversion is exact (8 MB)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "confmat.npy"), result.detach().to("cpu", torch.float64).numpy())
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (default: WORLD_SIZE under a launcher, else 1)")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed update steps")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-baseline", action="store_true", help="skip the in-run reference-emulation baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure compute_ms on its own and run the reference-emulation baseline (vs_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed region's result (the synced confusion matrix) to DIR/confmat.npy")
+    ap.add_argument("--no-baseline", action="store_true",
+                    help="with --full: skip the in-run reference-emulation baseline")
     ap.add_argument("--ring-mb", type=int, default=DEFAULT_RING_MB, help="size of the input ring (MB)")
     args = ap.parse_args()
 
@@ -147,22 +169,25 @@ def main() -> None:
 
     ours = MulticlassConfusionMatrix(num_classes=NUM_CLASSES).to(device)
     ref = None
-    if not args.no_baseline:
+    if args.full and not args.no_baseline:
         from benchmarks.reference_path import ReferenceEmulatedConfusionMatrix
 
         ref = ReferenceEmulatedConfusionMatrix(NUM_CLASSES, device)
     _warm(ours, preds, target, args.warmup)
-    t_ours, cms_ours, res_ours, phases = _timed(ours, preds, target, args.steps, args.warmup, device, world)
+    t_ours, cms_ours, res_ours, phases = _timed(ours, preds, target, args.steps, args.warmup, device, world, args.full)
     comms = comm_stats()
     t_ours = _max_over_ranks(t_ours, device, world)
-    cms_ours = _max_over_ranks(cms_ours, device, world)
+    if cms_ours is not None:
+        cms_ours = _max_over_ranks(cms_ours, device, world)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, res_ours)
     phases = {k: round(_max_over_ranks(v, device, world), 4) for k, v in phases.items()}  # slowest rank per phase
 
     base_val = None
     t_ref = cms_ref = None
     if ref is not None:
         _warm(ref, preds, target, args.warmup)
-        t_ref, cms_ref, res_ref, _ = _timed(ref, preds, target, args.steps, args.warmup, device, world)
+        t_ref, cms_ref, res_ref, _ = _timed(ref, preds, target, args.steps, args.warmup, device, world, True)
         t_ref = _max_over_ranks(t_ref, device, world)
         cms_ref = _max_over_ranks(cms_ref, device, world)
         if not torch.equal(res_ref.to(res_ours.device), res_ours):
@@ -178,7 +203,7 @@ def main() -> None:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(t_ours / args.steps * 1e3, 4),
+            "ms_per_step": round(t_ours / args.steps * 1e3, 6),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": round(value / base_val, 3) if base_val else None,
@@ -190,7 +215,8 @@ def main() -> None:
                 "seq_len": 1,
                 "parallelism": f"dp{world}",
             },
-            "compute_ms": round(cms_ours, 4),
+            "full": args.full,
+            "compute_ms": round(cms_ours, 4) if cms_ours is not None else None,
             "phases_ms_max_over_ranks": phases,
             "input_ring_mb": round(len(preds) * BATCH * NUM_CLASSES * 2 / 2**20, 1),
             "dist": {

@@ -22,7 +22,7 @@ def test_bench_two_rank_gloo_contract(tmp_path):
     env = dict(os.environ, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-           "2", "--warmup", "1", "--ring-mb", "8"]
+           "2", "--warmup", "1", "--ring-mb", "8", "--full"]
     res = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=580)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -56,6 +56,33 @@ def test_bench_self_launches_n_ranks(tmp_path):
     assert out["n_gpus"] == 2 and out["dist"]["world_size_seen"] == 2
     assert out["config"]["parallelism"] == "dp2"
     assert out["dist"]["engine_collectives"]["all_reduce"] >= 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run reports the headline only (no baseline, no separate compute timing) and ``--dump-outputs`` writes
+    the timed region's result; a ``--full`` run on the same arguments sees the same inputs, so it dumps the same."""
+    import numpy as np
+
+    outs = []
+    for name, extra in (("plain", ()), ("full", ("--full",))):
+        res = _self_launch(tmp_path, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--ring-mb", "8",
+                           "--dump-outputs", str(tmp_path / name), *extra)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, res.stdout
+        outs.append(json.loads(lines[0]))
+        assert sorted(os.listdir(tmp_path / name)) == ["confmat.npy"]
+    plain, full = outs
+    for out in outs:
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "updates/s" and out["dtype"] == "bf16"
+        assert out["higher_is_better"] is True and out["metric"] == "metric-updates/sec (whole node)"
+        assert abs(out["value"] * out["ms_per_step"] / 1e3 - 1.0) < 1e-2  # one rank: value = steps / elapsed
+    assert plain["vs_baseline"] is None and plain["compute_ms"] is None and plain["baseline"]["value"] is None
+    assert full["vs_baseline"] is not None and full["compute_ms"] > 0 and full["baseline"]["value"] > 0
+    a, b = np.load(tmp_path / "plain" / "confmat.npy"), np.load(tmp_path / "full" / "confmat.npy")
+    assert a.dtype == np.float64 and a.shape == (1000, 1000)
+    assert a.sum() == 3 * 8192  # exactly --steps updates of 8192 rows each reached the result
+    assert np.array_equal(a, b)
 
 
 def test_bench_world_size_mismatch_exits_nonzero(tmp_path):

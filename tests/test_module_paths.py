@@ -1,35 +1,23 @@
 """Every reference module path resolves, and carries the public names the reference defines there.
 
-The list of (module, names) pairs is taken from the reference tree when it is mounted (``/root/reference``);
-otherwise the alias table alone is checked.
+The (module, names) pairs are the fixture ``tests/golden/reference_module_names.json``
+(``tools/extract_reference_module_names.py``: parsed with ``ast`` from the reference's sources).
 """
-import ast
 import importlib
+import json
 import os
 
 import pytest
 
 from torchmetrics_amd import _module_aliases
 
-REF = "/root/reference/src/torchmetrics"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_module_names.json")
 
 
 def _reference_modules():
-    out = []
-    if not os.path.isdir(REF):
-        return out
-    for root, _, files in os.walk(REF):
-        for f in sorted(files):
-            if not f.endswith(".py"):
-                continue
-            rel = os.path.relpath(os.path.join(root, f), REF)[:-3].replace(os.sep, ".")
-            if rel.endswith("__init__"):
-                rel = rel[: -len(".__init__")] if rel != "__init__" else ""
-            tree = ast.parse(open(os.path.join(root, f)).read())
-            names = [n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.ClassDef))
-                     and not n.name.startswith("_")]
-            out.append(("torchmetrics_amd" + ("." + rel if rel else ""), names))
-    return out
+    with open(GOLDEN) as f:
+        data = json.load(f)
+    return [("torchmetrics_amd" + ("." + rel if rel else ""), names) for rel, names in sorted(data.items())]
 
 
 @pytest.mark.parametrize("alias", sorted(_module_aliases.aliases()))
@@ -38,10 +26,11 @@ def test_alias_imports(alias):
     assert mod.__name__ == alias
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
 def test_reference_public_names_resolve():
+    modules = _reference_modules()
+    assert len(modules) > 100, len(modules)
     missing = []
-    for mod_name, names in _reference_modules():
+    for mod_name, names in modules:
         mod = importlib.import_module(mod_name)
         missing += [f"{mod_name}.{n}" for n in names if not hasattr(mod, n)]
     assert not missing, missing

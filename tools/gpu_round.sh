@@ -4,6 +4,8 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+LOGS=${LOGS:-logs}  # where the bench step keeps its log; set LOGS to collect it elsewhere
+mkdir -p "$LOGS"
 STEP=${1:-all}
 if [[ $STEP == all || $STEP == test || $STEP == quick ]]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1 || { tail -40 gpurun_out/pytest_gpu.log; exit 1; }
@@ -14,8 +16,9 @@ if [[ $STEP == all || $STEP == smoke ]]; then
   tail -2 gpurun_out/smoke.log
 fi
 if [[ $STEP == all || $STEP == bench || $STEP == quick ]]; then
-  timeout -k 10 600 python bench.py > gpurun_out/bench.log 2>&1 || { tail -40 gpurun_out/bench.log; exit 1; }
-  tail -1 gpurun_out/bench.log
+  # --full: the record of a round carries vs_baseline and compute_ms, which a plain run no longer measures
+  timeout -k 10 600 python bench.py --full > "$LOGS/bench.log" 2>&1 || { tail -40 "$LOGS/bench.log"; exit 1; }
+  tail -1 "$LOGS/bench.log"
 fi
 if [[ $STEP == all || $STEP == prof ]]; then
   cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 5 > $GRAFT_REPO_ROOT/gpurun_out/prof.log 2>&1 || { tail -40 $GRAFT_REPO_ROOT/gpurun_out/prof.log; exit 1; }
