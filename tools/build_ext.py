@@ -22,6 +22,8 @@ BUILD = ROOT / "build" / "obj"
 OUT = ROOT / "torchmetrics_amd" / "_C" / "libtm_amd.so"
 FAST_SRC = CSRC / "bindings" / "fastcall.cpp"
 FAST_OUT = ROOT / "torchmetrics_amd" / "_C" / "_fastcall.so"
+# sources built without the packed fp32 VALU forms (v_pk_{add,mul,fma}_f32): plain per-lane fp32 math only
+NO_PACKED_FP32 = {"image/ssim3d.hip"}
 
 
 def _torch_paths():
@@ -72,6 +74,8 @@ def compile_one(src: Path, arch: str, force: bool, hdr_mtime: float) -> Path:
         "-o",
         str(obj),
     ]
+    if src.relative_to(CSRC).as_posix() in NO_PACKED_FP32:
+        cmd[1:1] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     if src.suffix == ".cpp":
         cmd.insert(1, "-x")
         cmd.insert(2, "hip")

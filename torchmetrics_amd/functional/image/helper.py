@@ -60,10 +60,8 @@ def _uniform_filter(inputs: Tensor, window_size: int) -> Tensor:
 
 
 def _window_1d(kernel_size: Sequence[int], sigma: Sequence[float], gaussian: bool, dtype: torch.dtype,
-               device: torch.device) -> Tuple[Tensor, Tensor]:
-    """Separable window taps (rows, cols) for the fused SSIM / UQI kernel."""
+               device: torch.device) -> Tuple[Tensor, ...]:
+    """Separable window taps, one vector per spatial dim (rows, cols or depth, rows, cols), for the fused kernels."""
     if gaussian:
-        return _gaussian(kernel_size[0], sigma[0], dtype, device)[0], _gaussian(kernel_size[1], sigma[1], dtype,
-                                                                                 device)[0]
-    return (torch.full((kernel_size[0],), 1.0 / kernel_size[0], dtype=dtype, device=device),
-            torch.full((kernel_size[1],), 1.0 / kernel_size[1], dtype=dtype, device=device))
+        return tuple(_gaussian(k, s, dtype, device)[0] for k, s in zip(kernel_size, sigma))
+    return tuple(torch.full((k,), 1.0 / k, dtype=dtype, device=device) for k in kernel_size)

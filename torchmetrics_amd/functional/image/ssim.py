@@ -1,8 +1,9 @@
 """SSIM, MS-SSIM and UQI (reference ``F/image/ssim.py:26-528``, ``F/image/uqi.py``).
 
-The 2-D per-image scores run through the fused HIP window kernel (``csrc/image/ssim.hip``) on ROCm: it evaluates the
-valid windows straight from the unpadded images (the reference's reflect-pad + crop yields exactly those windows).
-The explicit pad / grouped-convolution formulation below is kept for what the kernel does not cover: 3-D volumes,
+The per-image scores run through the fused HIP window kernels on ROCm (``csrc/image/ssim.hip`` for 2-D images,
+``csrc/image/ssim3d.hip`` for 3-D volumes): they evaluate the valid windows straight from the unpadded inputs (the
+reference's reflect-pad + crop yields exactly those windows).  The explicit pad / grouped-convolution formulation
+below is kept for what the kernels do not cover: depth windows over 11, in-plane windows over 33,
 ``return_full_image`` maps, ``reduction='none'`` UQI maps and autograd.
 """
 from typing import List, Optional, Sequence, Tuple, Union
@@ -93,6 +94,29 @@ def _fused_means(preds: Tensor, target: Tensor, wh: Tensor, ww: Tensor, c1, c2, 
     return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
 
 
+def _fused3d_ok(preds: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+    return (
+        preds.ndim == 5
+        and preds.is_cuda
+        and not (preds.requires_grad and torch.is_grad_enabled())
+        and max(ks[0], gauss_ks[0]) <= 11
+        and max(*ks[1:], *gauss_ks[1:]) <= 33
+        and all(n >= max(k, g) for n, k, g in zip(preds.shape[2:], ks, gauss_ks))
+        and preds.shape[0] * preds.shape[1] <= 65535
+    )
+
+
+def _fused3d_means(preds: Tensor, target: Tensor, taps: Sequence[Tensor], c1, c2):
+    """Per-volume mean (over channels and valid windows) of the SSIM map and of the contrast sensitivity."""
+    b, c, d, h, w = preds.shape
+    acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
+    consts = torch.stack([torch.as_tensor(v, dtype=acc, device=preds.device) for v in (c1, c2, 0.0)])
+    part = ops.ssim3d_partials(preds.reshape(b * c, d, h, w), target.reshape(b * c, d, h, w), *taps, consts)
+    n = c * (d - taps[0].numel() + 1) * (h - taps[1].numel() + 1) * (w - taps[2].numel() + 1)
+    sums = part.sum(1).reshape(b, c, 2).sum(1) / n
+    return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
+
+
 def _ssim_update(
     preds: Tensor,
     target: Tensor,
@@ -114,6 +138,11 @@ def _ssim_update(
     if not return_full_image and _fused_ok(preds, ks, gauss_ks) and (gaussian_kernel or ks == gauss_ks):
         wh, ww = _window_1d(gauss_ks if gaussian_kernel else ks, sg, gaussian_kernel, preds.dtype, preds.device)
         sim, cs = _fused_means(preds, target, wh, ww, c1, c2, 0.0, ops.SSIM_MODE)
+        return (sim, cs) if return_contrast_sensitivity else sim
+    if not return_full_image and _fused3d_ok(preds, ks, gauss_ks) and (gaussian_kernel or ks == gauss_ks):
+        acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
+        taps = _window_1d(gauss_ks if gaussian_kernel else ks, sg, gaussian_kernel, acc, preds.device)
+        sim, cs = _fused3d_means(preds, target, taps, c1, c2)
         return (sim, cs) if return_contrast_sensitivity else sim
     return _ssim_update_conv(preds, target, gaussian_kernel, ks, sg, gauss_ks, c1, c2, return_full_image,
                              return_contrast_sensitivity)

@@ -1226,6 +1226,24 @@ def ssim2d_partials(x: Tensor, y: Tensor, wh: Tensor, ww: Tensor, c12: Tensor, m
     return _cpu.ssim2d_partials(x, y, wh, ww, c12, mode)
 
 
+def ssim3d_partials(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c12: Tensor,
+                    depth_chunk: int = 0) -> Tensor:
+    """Per-plane sums of SSIM and contrast sensitivity over all windows fully inside the volume.
+
+    ``x``/``y``: ``[P, D, H, W]``; ``wd``/``wh``/``ww``: separable window weights of dims 1, 2, 3 (``wd`` at most 11
+    odd taps, ``wh``/``ww`` at most 33 on ROCm); ``c12``: ``(c1, c2, eps)`` as a tensor (may live on the device).
+    ``depth_chunk`` forces the output slices per block of the ROCm kernel (0: chosen from the CU count).  Returns
+    ``[P, T, 2]`` partial sums (``T`` blocks per plane on ROCm, 1 on the CPU); callers sum dim 1.
+    """
+    if x.is_cuda:
+        acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+            x, y = x.float(), y.float()
+        wd, wh, ww, c12 = (t.to(device=x.device, dtype=acc).contiguous() for t in (wd, wh, ww, c12))
+        return _ops().ssim3d_partials(x.contiguous(), y.contiguous(), wd, wh, ww, c12, depth_chunk)
+    return _cpu.ssim3d_partials(x, y, wd, wh, ww, c12)
+
+
 # ------------------------------------------------------------------------------------------------------- detection
 BOX_IOU, BOX_GIOU, BOX_DIOU, BOX_CIOU = range(4)
 

@@ -318,6 +318,23 @@ def ssim2d_partials(x: Tensor, y: Tensor, wh: Tensor, ww: Tensor, c12: Tensor, m
     return torch.stack([val.flatten(1).sum(1), cs.flatten(1).sum(1)], -1).unsqueeze(1)
 
 
+def ssim3d_partials(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c12: Tensor) -> Tensor:
+    """Valid-window SSIM / contrast-sensitivity sums per ``[D, H, W]`` plane via one depthwise ``conv3d``."""
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    x, y = x.to(acc).unsqueeze(1), y.to(acc).unsqueeze(1)
+    k = (wd.to(acc)[:, None, None] * wh.to(acc)[None, :, None] * ww.to(acc)[None, None, :])[None, None]
+    maps = torch.cat([x, y, x * x, y * y, x * y], 1)  # [P, 5, D, H, W]
+    m = torch.nn.functional.conv3d(maps, k.expand(5, 1, -1, -1, -1), groups=5)
+    mx, my, exx, eyy, exy = m.unbind(1)
+    mxx, myy, mxy = mx * mx, my * my, mx * my
+    sxx, syy, sxy = (exx - mxx).clamp(min=0), (eyy - myy).clamp(min=0), exy - mxy
+    c1, c2 = (float(v) for v in c12.to(acc).cpu()[:2])
+    upper, lower = 2 * sxy + c2, sxx + syy + c2
+    val = ((2 * mxy + c1) * upper) / ((mxx + myy + c1) * lower)
+    cs = upper / lower
+    return torch.stack([val.flatten(1).sum(1), cs.flatten(1).sum(1)], -1).unsqueeze(1)
+
+
 def box_pairwise(a: Tensor, b: Tensor, op: int, aligned: bool) -> Tensor:
     acc = torch.float64 if a.dtype == torch.float64 else torch.float32
     out_dtype = a.dtype if a.is_floating_point() else torch.float32
