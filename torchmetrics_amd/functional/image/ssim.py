@@ -2,9 +2,11 @@
 
 The per-image scores run through the fused HIP window kernels on ROCm (``csrc/image/ssim.hip`` for 2-D images,
 ``csrc/image/ssim3d.hip`` for 3-D volumes): they evaluate the valid windows straight from the unpadded inputs (the
-reference's reflect-pad + crop yields exactly those windows).  The explicit pad / grouped-convolution formulation
-below is kept for what the kernels do not cover: depth windows over 11, in-plane windows over 33,
-``return_full_image`` maps, ``reduction='none'`` UQI maps and autograd.
+reference's reflect-pad + crop yields exactly those windows).  2-D SSIM / MS-SSIM of ROCm inputs that require a
+gradient (``1 - ssim`` as a training loss) stay on that kernel and take their backward from its transposed twin,
+``csrc/image/ssim_grad.hip``, for windows up to 15.  The explicit pad / grouped-convolution formulation below is kept
+for what the kernels do not cover: depth windows over 11, in-plane windows over 33 (over 15 with a gradient),
+``return_full_image`` maps, ``reduction='none'`` UQI maps, and autograd on the CPU, on volumes and of UQI.
 """
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -72,24 +74,48 @@ def _data_range_consts(preds: Tensor, target: Tensor, data_range, k1: float, k2:
     return preds, target, (k1 * dr) ** 2, (k2 * dr) ** 2
 
 
-def _fused_ok(preds: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+def _window_fits(preds: Tensor, ks: Sequence[int], gauss_ks: Sequence[int], limit: int) -> bool:
     return (
         preds.ndim == 4
-        and not (preds.requires_grad and torch.is_grad_enabled())
-        and max(ks) <= 33
-        and max(gauss_ks) <= 33
+        and max(ks) <= limit
+        and max(gauss_ks) <= limit
         and preds.shape[-2] >= max(ks[0], gauss_ks[0])
         and preds.shape[-1] >= max(ks[1], gauss_ks[1])
     )
 
 
-def _fused_means(preds: Tensor, target: Tensor, wh: Tensor, ww: Tensor, c1, c2, eps: float, mode: int):
-    """Per-image mean (over channels and valid windows) of the SSIM/UQI map and of the contrast sensitivity."""
+def _fused_ok(preds: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+    """The forward-only window kernel applies (SSIM, UQI, SCC, VIF): no gradient wanted, windows up to 33."""
+    return not (preds.requires_grad and torch.is_grad_enabled()) and _window_fits(preds, ks, gauss_ks, 33)
+
+
+def _wants_grad(preds: Tensor, target: Tensor) -> bool:
+    return torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad)
+
+
+def _fused_grad_ok(preds: Tensor, target: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+    """The differentiable kernel pair applies (SSIM only): ROCm, a gradient wanted, windows up to 15."""
+    return (
+        preds.is_cuda
+        and _wants_grad(preds, target)
+        and _window_fits(preds, ks, gauss_ks, ops.SSIM_GRAD_MAX_WINDOW)
+        and preds.shape[0] * preds.shape[1] <= 65535
+    )
+
+
+def _fused_means(preds: Tensor, target: Tensor, wh: Tensor, ww: Tensor, c1, c2, eps: float, mode: int,
+                 grad: bool = False):
+    """Per-image mean (over channels and valid windows) of the SSIM/UQI map and of the contrast sensitivity;
+    ``grad``: through the differentiable kernel pair (SSIM mode, ROCm)."""
     b, c, h, w = preds.shape
     acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
     consts = torch.stack([torch.as_tensor(v, dtype=acc, device=preds.device) for v in (c1, c2, eps)])
-    part = ops.ssim2d_partials(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), wh, ww, consts, mode)
     n = c * (h - wh.numel() + 1) * (w - ww.numel() + 1)
+    if grad:  # consts keeps the graph of a data_range=None c1 / c2 (as_tensor and stack are differentiable)
+        sums = ops.ssim2d_sums_grad(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), wh, ww, consts)
+        sums = sums.reshape(b, c, 2).sum(1) / n
+        return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
+    part = ops.ssim2d_partials(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), wh, ww, consts, mode)
     sums = part.sum(1).reshape(b, c, 2).sum(1) / n
     return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
 
@@ -135,9 +161,12 @@ def _ssim_update(
         raise ValueError("Arguments `return_full_image` and `return_contrast_sensitivity` are mutually exclusive.")
     preds, target, c1, c2 = _data_range_consts(preds, target, data_range, k1, k2)
     gauss_ks = [int(3.5 * s + 0.5) * 2 + 1 for s in sg]
-    if not return_full_image and _fused_ok(preds, ks, gauss_ks) and (gaussian_kernel or ks == gauss_ks):
+    grad = _fused_grad_ok(preds, target, ks, gauss_ks)
+    # a ROCm target that alone wants a gradient must not take the forward-only kernel either
+    fwd = _fused_ok(preds, ks, gauss_ks) and not (preds.is_cuda and _wants_grad(preds, target))
+    if not return_full_image and (grad or fwd) and (gaussian_kernel or ks == gauss_ks):
         wh, ww = _window_1d(gauss_ks if gaussian_kernel else ks, sg, gaussian_kernel, preds.dtype, preds.device)
-        sim, cs = _fused_means(preds, target, wh, ww, c1, c2, 0.0, ops.SSIM_MODE)
+        sim, cs = _fused_means(preds, target, wh, ww, c1, c2, 0.0, ops.SSIM_MODE, grad)
         return (sim, cs) if return_contrast_sensitivity else sim
     if not return_full_image and _fused3d_ok(preds, ks, gauss_ks) and (gaussian_kernel or ks == gauss_ks):
         acc = torch.float64 if preds.dtype == torch.float64 else torch.float32

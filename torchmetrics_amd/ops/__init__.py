@@ -1226,6 +1226,55 @@ def ssim2d_partials(x: Tensor, y: Tensor, wh: Tensor, ww: Tensor, c12: Tensor, m
     return _cpu.ssim2d_partials(x, y, wh, ww, c12, mode)
 
 
+SSIM_GRAD_MAX_WINDOW = 15  # kMaxK of csrc/image/ssim_grad.hip
+
+
+def ssim2d_backward(x: Tensor, y: Tensor, wh: Tensor, ww: Tensor, c12: Tensor, g: Tensor, need_y: bool,
+                    need_c: bool) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """Gradient of the per-plane SSIM-mode sums of :func:`ssim2d_partials` (``csrc/image/ssim_grad.hip``, ROCm only).
+
+    ``g``: ``[P, 2]`` upstream gradient of each plane's (sum SSIM, sum CS); the other arguments as for the forward,
+    windows up to ``SSIM_GRAD_MAX_WINDOW``.  Returns ``(grad_x, grad_y or None, [P, T, 2] per-tile partials of
+    (d/dc1, d/dc2) or None)``.
+    """
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    wh, ww, c12, g = (t.to(device=x.device, dtype=acc).contiguous() for t in (wh, ww, c12, g))
+    gx, gy, gc = _ops().ssim2d_backward(x.contiguous(), y.contiguous(), wh, ww, c12, g, need_y, need_c)
+    return gx, (gy if need_y else None), (gc if need_c else None)
+
+
+class _SSIMSums(torch.autograd.Function):
+    """Autograd wrapper: forward = the fused window kernel (per-plane sums of SSIM and CS), backward = the fused
+    transposed-window kernel, which recomputes the window statistics from the two saved inputs."""
+
+    @staticmethod
+    def forward(ctx, x, y, wh, ww, c12):  # noqa: D102
+        ctx.save_for_backward(x, y, wh, ww, c12)
+        return ssim2d_partials(x, y, wh, ww, c12, SSIM_MODE).sum(1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):  # noqa: D102
+        x, y, wh, ww, c12 = ctx.saved_tensors
+        gx, gy, gc = ssim2d_backward(x, y, wh, ww, c12, g, ctx.needs_input_grad[1], ctx.needs_input_grad[4])
+        if not ctx.needs_input_grad[0]:
+            gx = None
+        if gc is not None:  # (d/dc1, d/dc2, d/deps = 0), carried on by torch to whatever c1 / c2 were made from
+            gc = torch.cat([gc.sum((0, 1)), gc.new_zeros(c12.numel() - 2)]).to(c12.dtype)
+        return gx, gy, None, None, gc
+
+
+def ssim2d_sums_grad(x: Tensor, y: Tensor, wh: Tensor, ww: Tensor, c12: Tensor) -> Tensor:
+    """Differentiable per-plane ``[P, 2]`` sums of SSIM and contrast sensitivity over the valid windows of ROCm
+    ``[P, H, W]`` planes (fp32 / fp64 / fp16 / bf16): gradients flow to ``x``, ``y`` and ``c12`` through the fused
+    HIP kernels, forward and backward."""
+    if not x.is_cuda:
+        raise ValueError("ssim2d_sums_grad serves ROCm tensors; CPU tensors take the convolution formulation")
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    return _SSIMSums.apply(x.contiguous(), y.contiguous(), wh.to(acc), ww.to(acc),
+                           c12.to(device=x.device, dtype=acc))
+
+
 def ssim3d_partials(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c12: Tensor,
                     depth_chunk: int = 0) -> Tensor:
     """Per-plane sums of SSIM and contrast sensitivity over all windows fully inside the volume.
