@@ -4,9 +4,11 @@ The per-image scores run through the fused HIP window kernels on ROCm (``csrc/im
 ``csrc/image/ssim3d.hip`` for 3-D volumes): they evaluate the valid windows straight from the unpadded inputs (the
 reference's reflect-pad + crop yields exactly those windows).  2-D SSIM / MS-SSIM of ROCm inputs that require a
 gradient (``1 - ssim`` as a training loss) stay on that kernel and take their backward from its transposed twin,
-``csrc/image/ssim_grad.hip``, for windows up to 15.  The explicit pad / grouped-convolution formulation below is kept
-for what the kernels do not cover: depth windows over 11, in-plane windows over 33 (over 15 with a gradient),
-``return_full_image`` maps, ``reduction='none'`` UQI maps, and autograd on the CPU, on volumes and of UQI.
+``csrc/image/ssim_grad.hip``, for windows up to 15; 3-D volumes that require one likewise keep the volume kernel and
+take their backward from the two launches of ``csrc/image/ssim3d_grad.hip`` (in-plane windows up to 15, depth windows
+up to 11).  The explicit pad / grouped-convolution formulation below is kept for what the kernels do not cover: depth
+windows over 11, in-plane windows over 33 (over 15 with a gradient), ``return_full_image`` maps, ``reduction='none'``
+UQI maps, and autograd on the CPU and of UQI.
 """
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -120,25 +122,39 @@ def _fused_means(preds: Tensor, target: Tensor, wh: Tensor, ww: Tensor, c1, c2, 
     return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
 
 
-def _fused3d_ok(preds: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+def _window3d_fits(preds: Tensor, ks: Sequence[int], gauss_ks: Sequence[int], in_plane_limit: int) -> bool:
     return (
         preds.ndim == 5
         and preds.is_cuda
-        and not (preds.requires_grad and torch.is_grad_enabled())
         and max(ks[0], gauss_ks[0]) <= 11
-        and max(*ks[1:], *gauss_ks[1:]) <= 33
+        and max(*ks[1:], *gauss_ks[1:]) <= in_plane_limit
         and all(n >= max(k, g) for n, k, g in zip(preds.shape[2:], ks, gauss_ks))
         and preds.shape[0] * preds.shape[1] <= 65535
     )
 
 
-def _fused3d_means(preds: Tensor, target: Tensor, taps: Sequence[Tensor], c1, c2):
-    """Per-volume mean (over channels and valid windows) of the SSIM map and of the contrast sensitivity."""
+def _fused3d_ok(preds: Tensor, target: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+    """The forward-only volume kernel applies: ROCm, no gradient wanted by either input, in-plane windows up to 33."""
+    return not _wants_grad(preds, target) and _window3d_fits(preds, ks, gauss_ks, 33)
+
+
+def _fused3d_grad_ok(preds: Tensor, target: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+    """The differentiable volume kernels apply: ROCm, a gradient wanted, in-plane windows up to 15."""
+    return _wants_grad(preds, target) and _window3d_fits(preds, ks, gauss_ks, ops.SSIM_GRAD_MAX_WINDOW)
+
+
+def _fused3d_means(preds: Tensor, target: Tensor, taps: Sequence[Tensor], c1, c2, grad: bool = False):
+    """Per-volume mean (over channels and valid windows) of the SSIM map and of the contrast sensitivity; ``grad``:
+    through the differentiable kernels."""
     b, c, d, h, w = preds.shape
     acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
     consts = torch.stack([torch.as_tensor(v, dtype=acc, device=preds.device) for v in (c1, c2, 0.0)])
-    part = ops.ssim3d_partials(preds.reshape(b * c, d, h, w), target.reshape(b * c, d, h, w), *taps, consts)
     n = c * (d - taps[0].numel() + 1) * (h - taps[1].numel() + 1) * (w - taps[2].numel() + 1)
+    if grad:  # consts keeps the graph of a data_range=None c1 / c2 (as_tensor and stack are differentiable)
+        sums = ops.ssim3d_sums_grad(preds.reshape(b * c, d, h, w), target.reshape(b * c, d, h, w), *taps, consts)
+        sums = sums.reshape(b, c, 2).sum(1) / n
+        return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
+    part = ops.ssim3d_partials(preds.reshape(b * c, d, h, w), target.reshape(b * c, d, h, w), *taps, consts)
     sums = part.sum(1).reshape(b, c, 2).sum(1) / n
     return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
 
@@ -168,10 +184,12 @@ def _ssim_update(
         wh, ww = _window_1d(gauss_ks if gaussian_kernel else ks, sg, gaussian_kernel, preds.dtype, preds.device)
         sim, cs = _fused_means(preds, target, wh, ww, c1, c2, 0.0, ops.SSIM_MODE, grad)
         return (sim, cs) if return_contrast_sensitivity else sim
-    if not return_full_image and _fused3d_ok(preds, ks, gauss_ks) and (gaussian_kernel or ks == gauss_ks):
+    grad3d = _fused3d_grad_ok(preds, target, ks, gauss_ks)
+    if not return_full_image and (grad3d or _fused3d_ok(preds, target, ks, gauss_ks)) and \
+            (gaussian_kernel or ks == gauss_ks):
         acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
         taps = _window_1d(gauss_ks if gaussian_kernel else ks, sg, gaussian_kernel, acc, preds.device)
-        sim, cs = _fused3d_means(preds, target, taps, c1, c2)
+        sim, cs = _fused3d_means(preds, target, taps, c1, c2, grad3d)
         return (sim, cs) if return_contrast_sensitivity else sim
     return _ssim_update_conv(preds, target, gaussian_kernel, ks, sg, gauss_ks, c1, c2, return_full_image,
                              return_contrast_sensitivity)

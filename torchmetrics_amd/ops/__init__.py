@@ -1293,6 +1293,62 @@ def ssim3d_partials(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c1
     return _cpu.ssim3d_partials(x, y, wd, wh, ww, c12)
 
 
+SSIM3D_GRAD_MAX_DEPTH_WINDOW = 11  # kMaxKD of csrc/image/ssim3d_grad.hip; in-plane: SSIM_GRAD_MAX_WINDOW
+
+
+def ssim3d_backward(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c12: Tensor, g: Tensor, need_y: bool,
+                    need_c: bool, depth_chunk: int = 0) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """Gradient of the per-volume sums of :func:`ssim3d_partials` (``csrc/image/ssim3d_grad.hip``, ROCm only).
+
+    ``g``: ``[P, 2]`` upstream gradient of each volume's (sum SSIM, sum CS); the other arguments as for the forward,
+    depth windows up to ``SSIM3D_GRAD_MAX_DEPTH_WINDOW``, in-plane windows up to ``SSIM_GRAD_MAX_WINDOW``.
+    ``depth_chunk`` forces the slices per block of both launches (0: chosen from the CU count).  Returns ``(grad_x,
+    grad_y or None, [P, T, 2] per-block partials of (d/dc1, d/dc2) or None)``.
+
+    The two launches hand over the per-window coefficient volumes through device scratch that lives for the call:
+    5 (3 without ``need_y``) accumulation-dtype words per valid window, about 33 MB at 2 x 1 x 128^3 and 82 MB at
+    1 x 1 x 160 x 192 x 160 in fp32.
+    """
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    wd, wh, ww, c12, g = (t.to(device=x.device, dtype=acc).contiguous() for t in (wd, wh, ww, c12, g))
+    gx, gy, gc = _ops().ssim3d_backward(x.contiguous(), y.contiguous(), wd, wh, ww, c12, g, need_y, need_c,
+                                        depth_chunk)
+    return gx, (gy if need_y else None), (gc if need_c else None)
+
+
+class _SSIM3DSums(torch.autograd.Function):
+    """Autograd wrapper: forward = the fused volume kernel (per-volume sums of SSIM and CS), backward = the coefficient
+    and transposed-march kernels, which recompute the window statistics from the two saved inputs."""
+
+    @staticmethod
+    def forward(ctx, x, y, wd, wh, ww, c12):  # noqa: D102
+        ctx.save_for_backward(x, y, wd, wh, ww, c12)
+        return _ops().ssim3d_partials(x, y, wd, wh, ww, c12, 0).sum(1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):  # noqa: D102
+        x, y, wd, wh, ww, c12 = ctx.saved_tensors
+        gx, gy, gc = ssim3d_backward(x, y, wd, wh, ww, c12, g, ctx.needs_input_grad[1], ctx.needs_input_grad[5])
+        if not ctx.needs_input_grad[0]:
+            gx = None
+        if gc is not None:  # (d/dc1, d/dc2, d/deps = 0), carried on by torch to whatever c1 / c2 were made from
+            gc = torch.cat([gc.sum((0, 1)), gc.new_zeros(c12.numel() - 2)]).to(c12.dtype)
+        return gx, gy, None, None, None, gc
+
+
+def ssim3d_sums_grad(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c12: Tensor) -> Tensor:
+    """Differentiable per-volume ``[P, 2]`` sums of SSIM and contrast sensitivity over the valid windows of ROCm
+    ``[P, D, H, W]`` volumes (fp32 / fp64 / fp16 / bf16): gradients flow to ``x``, ``y`` and ``c12`` through the fused
+    HIP kernels, forward and backward."""
+    if not x.is_cuda:
+        raise ValueError("ssim3d_sums_grad serves ROCm tensors; CPU tensors take the convolution formulation")
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    wd, wh, ww = (t.to(device=x.device, dtype=acc).contiguous() for t in (wd, wh, ww))
+    return _SSIM3DSums.apply(x.contiguous(), y.contiguous(), wd, wh, ww,
+                             c12.to(device=x.device, dtype=acc).contiguous())
+
+
 # ------------------------------------------------------------------------------------------------------- detection
 BOX_IOU, BOX_GIOU, BOX_DIOU, BOX_CIOU = range(4)
 
