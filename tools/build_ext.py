@@ -23,7 +23,7 @@ OUT = ROOT / "torchmetrics_amd" / "_C" / "libtm_amd.so"
 FAST_SRC = CSRC / "bindings" / "fastcall.cpp"
 FAST_OUT = ROOT / "torchmetrics_amd" / "_C" / "_fastcall.so"
 # sources built without the packed fp32 VALU forms (v_pk_{add,mul,fma}_f32): plain per-lane fp32 math only
-NO_PACKED_FP32 = {"image/ssim3d.hip", "image/ssim_grad.hip", "image/ssim3d_grad.hip"}
+NO_PACKED_FP32 = {"image/ssim3d.hip", "image/ssim_grad.hip", "image/ssim3d_grad.hip", "image/ssim_map.hip"}
 
 
 def _torch_paths():

@@ -6,10 +6,13 @@ reference's reflect-pad + crop yields exactly those windows).  2-D SSIM / MS-SSI
 gradient (``1 - ssim`` as a training loss) stay on that kernel and take their backward from its transposed twin,
 ``csrc/image/ssim_grad.hip``, for windows up to 15; 3-D volumes that require one likewise keep the volume kernel and
 take their backward from the two launches of ``csrc/image/ssim3d_grad.hip`` (in-plane windows up to 15, depth windows
-up to 11).  The explicit pad / grouped-convolution formulation below is kept for what the kernels do not cover: depth
-windows over 11, in-plane windows over 33 (over 15 with a gradient), ``return_full_image`` maps, ``reduction='none'``
-UQI maps, and autograd on the CPU and of UQI.
+up to 11).  ``return_full_image`` maps of ROCm images and volumes, and ``reduction='none'`` UQI maps, come from the
+map kernels of ``csrc/image/ssim_map.hip``, which mirror the borders while they stage a tile and give the per-image
+score from the same launch.  The explicit pad / grouped-convolution formulation below is kept for what the kernels do
+not cover: depth windows over 11, in-plane windows over 33 (over 15 with a gradient), maps that require a gradient, and
+autograd on the CPU and of UQI.
 """
+import math
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -159,6 +162,32 @@ def _fused3d_means(preds: Tensor, target: Tensor, taps: Sequence[Tensor], c1, c2
     return sums[:, 0].to(preds.dtype), sums[:, 1].to(preds.dtype)
 
 
+_MAP_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)
+
+
+def _fused_map_ok(preds: Tensor, target: Tensor, ks: Sequence[int], gauss_ks: Sequence[int]) -> bool:
+    """A map kernel applies: ROCm image or volume, no gradient wanted by either input, windows within its limits."""
+    if not preds.is_cuda or _wants_grad(preds, target) or preds.dtype not in _MAP_DTYPES:
+        return False
+    if preds.ndim == 4:
+        return (_window_fits(preds, ks, gauss_ks, ops.SSIM_MAP_MAX_WINDOW)
+                and preds.shape[0] * preds.shape[1] <= 65535)
+    return _window3d_fits(preds, ks, gauss_ks, ops.SSIM_MAP_MAX_WINDOW)
+
+
+def _fused_map(preds: Tensor, target: Tensor, taps: Sequence[Tensor], c1, c2) -> Tuple[Tensor, Tensor]:
+    """``(per_image, full)`` of ``_ssim_update_conv(..., return_full_image=True)`` from one map-kernel launch."""
+    b, c = preds.shape[:2]
+    acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
+    consts = torch.stack([torch.as_tensor(v, dtype=acc, device=preds.device) for v in (c1, c2, 0.0)])
+    planes = (b * c, *preds.shape[2:])
+    op = ops.ssim2d_map if preds.ndim == 4 else ops.ssim3d_map
+    full, part = op(preds.reshape(planes), target.reshape(planes), *taps, consts)
+    n = c * math.prod(s - t.numel() + 1 for s, t in zip(preds.shape[2:], taps))  # the crop: windows fully inside
+    per_image = part[..., 0].sum(1).reshape(b, c).sum(1) / n
+    return per_image.to(preds.dtype), full.reshape(preds.shape)
+
+
 def _ssim_update(
     preds: Tensor,
     target: Tensor,
@@ -191,6 +220,10 @@ def _ssim_update(
         taps = _window_1d(gauss_ks if gaussian_kernel else ks, sg, gaussian_kernel, acc, preds.device)
         sim, cs = _fused3d_means(preds, target, taps, c1, c2, grad3d)
         return (sim, cs) if return_contrast_sensitivity else sim
+    if return_full_image and _fused_map_ok(preds, target, ks, gauss_ks) and (gaussian_kernel or ks == gauss_ks):
+        acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
+        taps = _window_1d(gauss_ks if gaussian_kernel else ks, sg, gaussian_kernel, acc, preds.device)
+        return _fused_map(preds, target, taps, c1, c2)
     return _ssim_update_conv(preds, target, gaussian_kernel, ks, sg, gauss_ks, c1, c2, return_full_image,
                              return_contrast_sensitivity)
 
@@ -386,6 +419,14 @@ def _uqi_compute(
             return total.to(preds.dtype)
         n = b * c * (h - kernel_size[0] + 1) * (w - kernel_size[1] + 1)
         return (total / n).to(preds.dtype)
+    if reduction in ("none", None) and square and _fused_map_ok(preds, target, list(kernel_size), [1, 1]):
+        b, c, h, w = preds.shape
+        wh, ww = _window_1d(kernel_size, sigma, True, preds.dtype, preds.device)
+        acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
+        consts = torch.tensor([0.0, 0.0, eps], dtype=acc, device=preds.device)
+        full, _ = ops.ssim2d_map(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), wh, ww, consts,
+                                 ops.UQI_MODE, reflect=False)
+        return full.reshape(b, c, *full.shape[1:])
     return reduce(_uqi_map(preds, target, kernel_size, sigma, eps), reduction)
 
 

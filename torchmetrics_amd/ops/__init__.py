@@ -1293,6 +1293,39 @@ def ssim3d_partials(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c1
     return _cpu.ssim3d_partials(x, y, wd, wh, ww, c12)
 
 
+SSIM_MAP_MAX_WINDOW = 33  # kMaxK of csrc/image/ssim_map.hip (in-plane; its depth windows go up to 11)
+
+
+def ssim2d_map(x: Tensor, y: Tensor, wh: Tensor, ww: Tensor, c12: Tensor, mode: int = SSIM_MODE,
+               reflect: bool = True) -> Tuple[Tensor, Tensor]:
+    """The SSIM (or UQI) map of ROCm ``[P, H, W]`` planes and its per-tile sums in one launch
+    (``csrc/image/ssim_map.hip``, ROCm only; fp32 / fp64 / fp16 / bf16, windows up to ``SSIM_MAP_MAX_WINDOW``).
+
+    ``reflect``: ``map`` is ``[P, H, W]``, the (odd) window centred on every pixel with the borders mirrored as
+    ``F.pad(mode="reflect")`` does; else ``[P, H-kh+1, W-kw+1]``, the windows fully inside the image.  ``part`` is
+    ``[P, T, 2]`` sums of (SSIM or UQI, contrast sensitivity) over the windows fully inside the image, as
+    :func:`ssim2d_partials` returns.  Returns ``(map in x.dtype, part)``.
+    """
+    if not x.is_cuda:
+        raise ValueError("ssim2d_map serves ROCm tensors; CPU tensors take the convolution formulation")
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    wh, ww, c12 = (t.to(device=x.device, dtype=acc).contiguous() for t in (wh, ww, c12))
+    return _ops().ssim2d_map(x.contiguous(), y.contiguous(), wh, ww, c12, mode, reflect)
+
+
+def ssim3d_map(x: Tensor, y: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, c12: Tensor,
+               depth_chunk: int = 0) -> Tuple[Tensor, Tensor]:
+    """The SSIM map ``[P, D, H, W]`` (mirrored borders) of ROCm volumes and its per-block sums in one launch
+    (``csrc/image/ssim_map.hip``, ROCm only): arguments as for :func:`ssim3d_partials`, odd windows, in-plane up to
+    ``SSIM_MAP_MAX_WINDOW``.  Returns ``(map in x.dtype, part [P, T, 2] over the windows fully inside the volume)``.
+    """
+    if not x.is_cuda:
+        raise ValueError("ssim3d_map serves ROCm tensors; CPU tensors take the convolution formulation")
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    wd, wh, ww, c12 = (t.to(device=x.device, dtype=acc).contiguous() for t in (wd, wh, ww, c12))
+    return _ops().ssim3d_map(x.contiguous(), y.contiguous(), wd, wh, ww, c12, depth_chunk)
+
+
 SSIM3D_GRAD_MAX_DEPTH_WINDOW = 11  # kMaxKD of csrc/image/ssim3d_grad.hip; in-plane: SSIM_GRAD_MAX_WINDOW
 
 
