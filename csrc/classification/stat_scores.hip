@@ -222,33 +222,172 @@ __global__ void __launch_bounds__(kBlock) mc_argmax_pipe_kernel(const scalar_t* 
 // any NaN (positive NaN ordinals sit above +inf, negative ones below -inf) and a max of +-0 (-0 == +0 ties by index).
 // Measured on MI355X (8192 x 1000 bf16, 8 blocks/CU): 5.2 us vs 8.1 us for the float-compare wave argmax, against a
 // 3.3 us back-to-back empty-launch floor -- the float compare made the kernel VALU-bound (tools/mb/confmat_mb.hip).
+// In front of it sits the raw-bit shortcut (wave_argmax_raw16), and a grid of one row per wave takes the loop-free
+// kOneRow form.  Measured on the 406 MB ring (tools/mb/confmat_ring_mb.hip, profiles/r07_confmat_ring_mb_after.jsonl,
+// 512-thread blocks, one row per wave): pure read 4.15 us, ordinal reduction 4.88 (label store instead of the atomic:
+// 4.70), raw-bit reduction 4.81 (4.59); all-negative rows 4.86 -> 4.78; in a slower state of the machine the two
+// reductions were level.  In bench.py's 200-step trace the kernel averages 5.17 us (median 5.16, p95 5.48, max 7.48),
+// 5.23 with the ordinal reduction in the loop-free form, where the looped ordinal kernel averaged 5.38 (5.36, 5.80,
+// 7.44) in the same run (profiles/r07_headline_kernel_200step_{parent,pr,pr_ord16}.txt).
 template <typename scalar_t>
 struct Ord16;
 template <>
 struct Ord16<c10::BFloat16> {
   static constexpr uint32_t kPosInf = 0xff80u, kNegInf = 0x007fu;
+  static constexpr uint32_t kRawPosInf = 0x7f80u, kRawNegInf = 0xff80u;
 };
 template <>
 struct Ord16<c10::Half> {
   static constexpr uint32_t kPosInf = 0xfc00u, kNegInf = 0x03ffu;
+  static constexpr uint32_t kRawPosInf = 0x7c00u, kRawNegInf = 0xfc00u;
 };
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  return static_cast<uint32_t>(__reduce_max_sync(~0ull, static_cast<int>(v ^ 0x80000000u))) ^ 0x80000000u;
+// The device library's DPP wave reduction, called directly (HIP declares it in amd_warp_sync_functions.h for its own
+// __reduce_max_sync).  __reduce_max_sync(~0ull, ...) on the sign-flipped value wraps the same call in two xors and a
+// run-time check of the mask against exec; with it the raw-bit kernel gained 0.03 us per launch on the ordinal one
+// where this form gained 0.07, and bench.py --steps 200 read 197.1 k updates/s where this form read 199.6-201.0 k
+// (separate runs, the parent at 190.1-190.2 k in each; profiles/r07_headline_summary.md).
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return __ockl_wfred_max_u32(v); }
+
+// The raw-bit shortcut in front of the ordinal map: three packed ops per 32-bit word on the raw halves and no mapped
+// copy of the row.  Non-negative floats order as signed int16 and every negative float is a negative int16, so a packed
+// signed max (v_pk_max_i16) is the lane's maximum wherever the lane holds a non-negative value; in an all-negative lane
+// it is the smallest pattern (v_pk_min_u16).  A packed unsigned max (v_pk_max_u16) proves there is no negative NaN
+// (patterns above -inf's).  Only that ONE value per lane is mapped to its ordinal.  The lane's first column holding it
+// comes from a no-match mask -- per word xor / v_pk_min_u16 with 1 / shift-or, bit i = word i's low half, bit 16 + i
+// its high half -- and, as in wave_argmax_ord16, one wave max over (ordinal << 16 | 0xffff - column) ends it.  The
+// result is exact under the ordinal path's own conditions (no NaN, the maximum not +-0); else false, and the caller
+// takes wave_argmax_ord16.  A lane past the row's last 16-byte chunk holds that last chunk again (see the kernel's
+// loads): it changes no maximum, and its columns are >= C, behind those of the chunk's real owner.
+__device__ __forceinline__ uint32_t pk_nonzero_u16(uint32_t x) {  // 1 in each half that is not 0
+  uint32_t t;  // (asm: the compiler rewrites min(x, 1) into two compares, two selects and a v_perm)
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(t) : "v"(x), "s"(0x00010001u));
+  return t;
 }
 
-constexpr int kOrdBlock = 512;  // 8 waves: half the workgroups of 256-thread blocks for the same waves (measured on
-                                // the 406 MB ring, tools/mb/confmat_ring_mb.hip: 5.06 us vs 5.38 us per 8192 x 1000)
+template <typename scalar_t, int kPer>
+__device__ __forceinline__ bool wave_argmax_raw16(const u32x4 (&cur)[kPer], int lane, int& bidx) {
+  s16x2 smx = {-32768, -32768};
+  u16x2 umx = {0, 0}, umn = {0xffff, 0xffff};
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t w = cur[j][k];
+      smx = __builtin_elementwise_max(smx, __builtin_bit_cast(s16x2, w));
+      umx = __builtin_elementwise_max(umx, __builtin_bit_cast(u16x2, w));
+      umn = __builtin_elementwise_min(umn, __builtin_bit_cast(u16x2, w));
+    }
+  }
+  const int ls = smx.x > smx.y ? smx.x : smx.y;
+  const uint32_t lu = umx.x > umx.y ? umx.x : umx.y;
+  const uint32_t ln = umn.x < umn.y ? umn.x : umn.y;
+  const bool lneg = ls < 0;
+  const uint32_t c = lneg ? ln : static_cast<uint32_t>(ls);  // the lane's maximum, as a raw pattern
+  const uint32_t ord = c ^ (lneg ? 0xffffu : 0x8000u);
+  const uint32_t cc = c | (c << 16);
+  uint32_t miss = 0;
+#pragma unroll
+  for (int j = kPer - 1; j >= 0; --j) {
+#pragma unroll
+    for (int k = 3; k >= 0; --k) miss = (miss << 1) | pk_nonzero_u16(cur[j][k] ^ cc);
+  }
+  // position 2 * i + half of the first hit in the lane's own order (one exists: c is one of the lane's halves)
+  constexpr uint32_t kWords = (1u << (4 * kPer)) - 1u;
+  const uint32_t hit = ~miss;
+  const int plo = 2 * __builtin_ctz((hit & kWords) | 0x10000u);
+  const int phi = 2 * __builtin_ctz(((hit >> 16) & kWords) | 0x10000u) + 1;
+  const int pos = plo < phi ? plo : phi;
+  const uint32_t col = lane * 8 + (pos >> 3) * (kWave * 8) + (pos & 7);
+  const uint32_t key = wave_max_u32((ord << 16) | (0xffffu - col));
+  const uint32_t kmax = key >> 16;
+  bidx = 0xffff - static_cast<int>(key & 0xffffu);
+  return kmax <= Ord16<scalar_t>::kPosInf && kmax != 0x8000u && kmax != 0x7fffu &&
+         !__any(lu > Ord16<scalar_t>::kRawNegInf);
+}
 
-template <typename scalar_t, typename target_t, int kPer, int kMode>
+// The ordinal reduction (and, under it, the float compare) on a row held in registers: torch.argmax's column.
+template <typename scalar_t, int kPer>
+__device__ __forceinline__ int wave_argmax_ord16(const u32x4 (&cur)[kPer], int lane, int nchunks) {
+  u16x2 mx = {0, 0}, mn = {0xffff, 0xffff};
+  uint32_t ordw[kPer][4];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int ci = lane + j * kWave;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t w = cur[j][k];
+      const s16x2 sw = __builtin_bit_cast(s16x2, w);
+      const uint32_t sgn = __builtin_bit_cast(uint32_t, static_cast<s16x2>(sw >> (s16x2){15, 15}));
+      const uint32_t o = w ^ (sgn | 0x80008000u);
+      ordw[j][k] = o;
+      if (ci < nchunks) {
+        const u16x2 ov = __builtin_bit_cast(u16x2, o);
+        mx = __builtin_elementwise_max(mx, ov);
+        mn = __builtin_elementwise_min(mn, ov);
+      }
+    }
+  }
+  const uint32_t lmax = mx.x > mx.y ? mx.x : mx.y;
+  const uint32_t lmin = mn.x < mn.y ? mn.x : mn.y;
+  uint32_t first = 0xffffu;  // lane's first column holding lmax (reverse scan: the last hit is the first column)
+#pragma unroll
+  for (int j = kPer - 1; j >= 0; --j) {
+    const int ci = lane + j * kWave;
+    if (ci < nchunks) {
+#pragma unroll
+      for (int k = 3; k >= 0; --k) {
+        const uint32_t o = ordw[j][k];
+        if ((o >> 16) == lmax) first = ci * 8 + 2 * k + 1;
+        if ((o & 0xffffu) == lmax) first = ci * 8 + 2 * k;
+      }
+    }
+  }
+  const uint32_t key = wave_max_u32((lmax << 16) | (0xffffu - first));
+  const uint32_t kmax = key >> 16;
+  const bool exact = kmax <= Ord16<scalar_t>::kPosInf && kmax != 0x8000u && kmax != 0x7fffu &&
+                     !__any(lmin < Ord16<scalar_t>::kNegInf);
+  int bidx = 0xffff - static_cast<int>(key & 0xffffu);
+  if (!exact) {  // wave-uniform, rare
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const int ci = lane + j * kWave;
+      if (ci < nchunks) {
+        const scalar_t* e = reinterpret_cast<const scalar_t*>(&cur[j]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float v = to_f32(e[k]);
+          if (argmax_better(v, ci * 8 + k, best, bi)) {
+            best = v;
+            bi = ci * 8 + k;
+          }
+        }
+      }
+    }
+    wave_argmax(best, bi);
+    bidx = bi;
+  }
+  return bidx;
+}
+
+constexpr int kOrdBlock = 512;  // 8 waves: half the workgroups of 256-thread blocks for the same waves.  Measured on
+                                // the 406 MB ring (tools/mb/confmat_ring_mb.hip, 8192 x 1000, one row per wave) with the
+                                // raw-bit reduction: 512 threads 4.81 us, 1024 threads 4.90; ordinal reduction: 256
+                                // threads 4.98, 512 4.88, 1024 5.00.  The pure read no longer favours 1024 (4.15 vs 4.13)
+
+// kOneRow: the grid covers N with at most one row per wave -- no next-row registers, no loop.  ord_only (the value 2 of
+// TM_AMD_MC_ORD16, an A/B knob) skips the raw-bit shortcut: the ordinal reduction on every row.
+template <typename scalar_t, typename target_t, int kPer, int kMode, bool kOneRow>
 __global__ void __launch_bounds__(kOrdBlock) mc_argmax_ord16_kernel(const scalar_t* __restrict__ preds,
                                                                  const target_t* __restrict__ target, long long N,
                                                                  int C, long long ignore, bool has_ignore,
                                                                  int64_t* __restrict__ out, int* __restrict__ flag,
-                                                                 int64_t* __restrict__ out2 = nullptr,
+                                                                 bool ord_only, int64_t* __restrict__ out2 = nullptr,
                                                                  int64_t* __restrict__ tn_st = nullptr,
                                                                  int64_t* __restrict__ fn_st = nullptr,
                                                                  long long tn_all = 0) {
@@ -264,84 +403,20 @@ __global__ void __launch_bounds__(kOrdBlock) mc_argmax_ord16_kernel(const scalar
   const long long nwaves = static_cast<long long>(gridDim.x) * (blockDim.x / kWave);
   const long long wave = (static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
   const int nchunks = C / 8;
-  u32x4 cur[kPer], nxt[kPer];
-  long long tcur = 0, tnxt = 0;
-  auto issue = [&](long long row, u32x4* buf, long long& t) {
+  auto issue = [&](long long row, u32x4 (&buf)[kPer], long long& t) {
     const u32x4* rp = reinterpret_cast<const u32x4*>(preds + row * C);
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
-      const int ci = lane + j * kWave;
-      if (ci < nchunks) buf[j] = __builtin_nontemporal_load(rp + ci);
+      const int ci = lane + j * kWave;  // past the row's end: the last chunk again (wave_argmax_raw16)
+      buf[j] = __builtin_nontemporal_load(rp + (ci < nchunks ? ci : nchunks - 1));
     }
     if (lane == 0) t = static_cast<long long>(target[row]);
   };
-  long long row = wave;
-  if (row < N) issue(row, cur, tcur);
-  for (; row < N; row += nwaves) {  // wave-uniform
-    const long long next = row + nwaves;
-    if (next < N) issue(next, nxt, tnxt);
-    u16x2 mx = {0, 0}, mn = {0xffff, 0xffff};
-    uint32_t ordw[kPer][4];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const int ci = lane + j * kWave;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t w = cur[j][k];
-        const s16x2 sw = __builtin_bit_cast(s16x2, w);
-        const uint32_t sgn = __builtin_bit_cast(uint32_t, static_cast<s16x2>(sw >> (s16x2){15, 15}));
-        const uint32_t o = w ^ (sgn | 0x80008000u);
-        ordw[j][k] = o;
-        if (ci < nchunks) {
-          const u16x2 ov = __builtin_bit_cast(u16x2, o);
-          mx = __builtin_elementwise_max(mx, ov);
-          mn = __builtin_elementwise_min(mn, ov);
-        }
-      }
-    }
-    const uint32_t lmax = mx.x > mx.y ? mx.x : mx.y;
-    const uint32_t lmin = mn.x < mn.y ? mn.x : mn.y;
-    uint32_t first = 0xffffu;  // lane's first column holding lmax (reverse scan: the last hit is the first column)
-#pragma unroll
-    for (int j = kPer - 1; j >= 0; --j) {
-      const int ci = lane + j * kWave;
-      if (ci < nchunks) {
-#pragma unroll
-        for (int k = 3; k >= 0; --k) {
-          const uint32_t o = ordw[j][k];
-          if ((o >> 16) == lmax) first = ci * 8 + 2 * k + 1;
-          if ((o & 0xffffu) == lmax) first = ci * 8 + 2 * k;
-        }
-      }
-    }
-    const uint32_t key = wave_max_u32((lmax << 16) | (0xffffu - first));
-    const uint32_t kmax = key >> 16;
-    const bool exact = kmax <= Ord16<scalar_t>::kPosInf && kmax != 0x8000u && kmax != 0x7fffu &&
-                       !__any(lmin < Ord16<scalar_t>::kNegInf);
-    int bidx = 0xffff - static_cast<int>(key & 0xffffu);
-    if (!exact) {  // wave-uniform, rare
-      float best = -INFINITY;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        const int ci = lane + j * kWave;
-        if (ci < nchunks) {
-          const scalar_t* e = reinterpret_cast<const scalar_t*>(&cur[j]);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const float v = to_f32(e[k]);
-            if (argmax_better(v, ci * 8 + k, best, bi)) {
-              best = v;
-              bi = ci * 8 + k;
-            }
-          }
-        }
-      }
-      wave_argmax(best, bi);
-      bidx = bi;
-    }
+  auto finish = [&](const u32x4 (&cur)[kPer], long long t) {
+    int bidx;
+    if (ord_only || !wave_argmax_raw16<scalar_t, kPer>(cur, lane, bidx))  // wave-uniform
+      bidx = wave_argmax_ord16<scalar_t, kPer>(cur, lane, nchunks);
     if (lane == 0) {
-      const long long t = tcur;
       bool ok = true;
       if (has_ignore && t == ignore) ok = false;
       else if (t < 0 || t >= C) {
@@ -373,6 +448,24 @@ __global__ void __launch_bounds__(kOrdBlock) mc_argmax_ord16_kernel(const scalar
         }
       }
     }
+  };
+  u32x4 cur[kPer];
+  long long tcur = 0;
+  long long row = wave;
+  if constexpr (kOneRow) {
+    if (row < N) {  // wave-uniform
+      issue(row, cur, tcur);
+      finish(cur, tcur);
+    }
+    return;
+  }
+  u32x4 nxt[kPer];
+  long long tnxt = 0;
+  if (row < N) issue(row, cur, tcur);
+  for (; row < N; row += nwaves) {  // wave-uniform
+    const long long next = row + nwaves;
+    if (next < N) issue(next, nxt, tnxt);
+    finish(cur, tcur);
 #pragma unroll
     for (int j = 0; j < kPer; ++j) cur[j] = nxt[j];
     tcur = tnxt;
@@ -1973,24 +2066,39 @@ void mc_update(const at::Tensor& preds, const at::Tensor& target, at::Tensor out
             const int cus = cu_count(preds.get_device());
             const long long want = (N + kBlock / kWave - 1) / (kBlock / kWave);
             const int grid = static_cast<int>(std::min<long long>(want, static_cast<long long>(cus) * pipe_override));
-            static const bool ord16_off = std::getenv("TM_AMD_MC_ORD16") && std::atoi(std::getenv("TM_AMD_MC_ORD16")) == 0;
+            // TM_AMD_MC_ORD16: 0 = float-compare pipe kernel, 2 = ordinal reduction on every row (no raw-bit shortcut).
+            // Read here only: mc_confmat_dual declines while it is set (forward() then comes through here), and
+            // mc_stats_direct ignores it -- the direct tp / fp / tn / fn update always takes the raw-bit shortcut.
+            static const int ord16_env = std::getenv("TM_AMD_MC_ORD16") ? std::atoi(std::getenv("TM_AMD_MC_ORD16")) : 1;
+            static const bool ord16_off = ord16_env == 0;
+            static const bool ord_only = ord16_env == 2;
             auto launch_pipe = [&](auto per_tag) {
               constexpr int P = decltype(per_tag)::value;
               if constexpr (sizeof(scalar_t) == 2) {
                 if (!ord16_off) {
                   const long long want16 = (N + kOrdBlock / kWave - 1) / (kOrdBlock / kWave);  // one row per wave
+                  // 4 x 512 threads per CU is 8 waves per SIMD: 8192 rows are exactly one row per wave on 256 CUs, which
+                  // the loop-free kernel takes (bench.py, 200 steps: 190.1 k -> 199.6 k updates/s, 196.5 k with
+                  // TM_AMD_MC_ORD16=2; 2 blocks per CU 183.6 k, 3: 188.0 k, 8: the same grid as 4;
+                  // profiles/r07_bench_headline_ab.txt)
                   static const int per_cu = [] {  // blocks per CU (TM_AMD_ORD16_BLOCKS_PER_CU: measurement knob)
                     const char* e = std::getenv("TM_AMD_ORD16_BLOCKS_PER_CU");
                     return e ? std::max(1, std::atoi(e)) : 4;
                   }();
                   const int grid16 =
                       static_cast<int>(std::min<long long>(want16, static_cast<long long>(cus) * per_cu));
-                  if (mode == kMcConfmat)
-                    hipLaunchKernelGGL((mc_argmax_ord16_kernel<scalar_t, target_t, P, kMcConfmat>), dim3(grid16),
-                                       dim3(kOrdBlock), 0, s, pp, tp, N, C, ignore_index, has_ignore, outp, flagp);
-                  else
-                    hipLaunchKernelGGL((mc_argmax_ord16_kernel<scalar_t, target_t, P, kMcStats>), dim3(grid16),
-                                       dim3(kOrdBlock), 0, s, pp, tp, N, C, ignore_index, has_ignore, outp, flagp);
+                  auto go = [&](auto mode_tag, auto one_tag) {
+                    hipLaunchKernelGGL(
+                        (mc_argmax_ord16_kernel<scalar_t, target_t, P, decltype(mode_tag)::value, decltype(one_tag)::value>),
+                        dim3(grid16), dim3(kOrdBlock), 0, s, pp, tp, N, C, ignore_index, has_ignore, outp, flagp,
+                        ord_only);
+                  };
+                  auto by_rows = [&](auto mode_tag) {  // one row per wave: the loop-free kernel
+                    if (grid16 == want16) go(mode_tag, std::true_type{});
+                    else go(mode_tag, std::false_type{});
+                  };
+                  if (mode == kMcConfmat) by_rows(std::integral_constant<int, kMcConfmat>{});
+                  else by_rows(std::integral_constant<int, kMcStats>{});
                   return;
                 }
               }
@@ -2116,13 +2224,17 @@ bool mc_stats_direct(const at::Tensor& preds, const at::Tensor& target, at::Tens
   const int per = static_cast<int>((row_bytes / 16 + kWave - 1) / kWave);
   TM_DISPATCH_TARGET(target.scalar_type(), "mc_stats_direct", [&] {
     const target_t* tg = reinterpret_cast<const target_t*>(target.data_ptr());
-    auto go = [&](auto scalar_tag, auto per_tag) {
+    auto launch = [&](auto scalar_tag, auto per_tag, auto one_tag) {
       using scalar_t = decltype(scalar_tag);
       constexpr int P = decltype(per_tag)::value;
-      hipLaunchKernelGGL((mc_argmax_ord16_kernel<scalar_t, target_t, P, kMcStatsDirect>), dim3(grid16),
-                         dim3(kOrdBlock), 0, s, reinterpret_cast<const scalar_t*>(preds.data_ptr()), tg, N,
-                         static_cast<int>(C), 0LL, false, tp.data_ptr<int64_t>(), flag.data_ptr<int>(),
+      hipLaunchKernelGGL((mc_argmax_ord16_kernel<scalar_t, target_t, P, kMcStatsDirect, decltype(one_tag)::value>),
+                         dim3(grid16), dim3(kOrdBlock), 0, s, reinterpret_cast<const scalar_t*>(preds.data_ptr()), tg,
+                         N, static_cast<int>(C), 0LL, false, tp.data_ptr<int64_t>(), flag.data_ptr<int>(), false,
                          fp.data_ptr<int64_t>(), tn.data_ptr<int64_t>(), fn.data_ptr<int64_t>(), N);
+    };
+    auto go = [&](auto scalar_tag, auto per_tag) {  // one row per wave: the loop-free kernel
+      if (grid16 == want16) launch(scalar_tag, per_tag, std::true_type{});
+      else launch(scalar_tag, per_tag, std::false_type{});
     };
     auto by_per = [&](auto scalar_tag) {
       if (per == 1) go(scalar_tag, std::integral_constant<int, 1>{});
@@ -2392,12 +2504,16 @@ bool mc_confmat_dual(const at::Tensor& preds, const at::Tensor& target, at::Tens
   auto s = stream();
   TM_DISPATCH_TARGET(target.scalar_type(), "mc_confmat_dual", [&] {
     const target_t* tp = reinterpret_cast<const target_t*>(target.data_ptr());
-    auto go = [&](auto* pp, auto per_tag) {
+    auto launch = [&](auto* pp, auto per_tag, auto one_tag) {
       using scalar_t = std::remove_const_t<std::remove_pointer_t<decltype(pp)>>;
       constexpr int P = decltype(per_tag)::value;
-      hipLaunchKernelGGL((mc_argmax_ord16_kernel<scalar_t, target_t, P, kMcConfmatDual>), dim3(grid16),
-                         dim3(kOrdBlock), 0, s, pp, tp, N, static_cast<int>(C), ignore_index, has_ignore,
-                         batch.data_ptr<int64_t>(), flag.data_ptr<int>(), global.data_ptr<int64_t>());
+      hipLaunchKernelGGL((mc_argmax_ord16_kernel<scalar_t, target_t, P, kMcConfmatDual, decltype(one_tag)::value>),
+                         dim3(grid16), dim3(kOrdBlock), 0, s, pp, tp, N, static_cast<int>(C), ignore_index, has_ignore,
+                         batch.data_ptr<int64_t>(), flag.data_ptr<int>(), false, global.data_ptr<int64_t>());
+    };
+    auto go = [&](auto* pp, auto per_tag) {  // one row per wave: the loop-free kernel
+      if (grid16 == want16) launch(pp, per_tag, std::true_type{});
+      else launch(pp, per_tag, std::false_type{});
     };
     auto by_per = [&](auto* pp) {
       if (per == 1) go(pp, std::integral_constant<int, 1>{});
