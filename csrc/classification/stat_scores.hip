@@ -2000,6 +2000,14 @@ bool finalize_pending(at::Tensor ws, at::Tensor not_prob, bool accumulate, int64
 //   target: int [N, X]
 //   mode 0: out = confmat [C, C] int64 (accumulated in place)
 //   mode 1: out = workspace [G, 3C+1] int64 (G = N if samplewise else 1); finalize with mc_stats_finalize
+// Float scores with a spatial axis of X >= kDenseMinX go to the channel-strided kernels of mc_dense.hip (f32 / f16 /
+// bf16; it declines f64).  Below that most lanes of its pixel tiles would idle, so small X keeps the kernels here.
+// TM_AMD_MC_DENSE=0 restores the old dispatch for every X (A/B runs).
+bool mc_dense_update(const at::Tensor& preds, const at::Tensor& target, at::Tensor out, at::Tensor flag,
+                     int64_t num_classes, int64_t ignore_index, bool has_ignore, int64_t mode, bool samplewise,
+                     int64_t top_k);
+constexpr long long kDenseMinX = 512;
+
 void mc_update(const at::Tensor& preds, const at::Tensor& target, at::Tensor out, at::Tensor flag, int64_t num_classes,
                int64_t ignore_index, bool has_ignore, int64_t mode, bool samplewise) {
   TM_CHECK_CUDA(preds);
@@ -2031,6 +2039,13 @@ void mc_update(const at::Tensor& preds, const at::Tensor& target, at::Tensor out
     TORCH_CHECK(K >= 1 && K <= 16, "mc_update: at most 16 predicted labels per item");
     TORCH_CHECK(mode == kMcStats || K == 1, "mc_update: confmat needs exactly one predicted label");
   }
+  static const bool dense_on = [] {
+    const char* e = std::getenv("TM_AMD_MC_DENSE");
+    return !(e && std::atoi(e) == 0);
+  }();
+  if (argmax && X >= kDenseMinX && dense_on &&
+      mc_dense_update(preds, target, out, flag, num_classes, ignore_index, has_ignore, mode, samplewise, 1))
+    return;
   const int nbins = mode == kMcConfmat ? C * C : 3 * C + 1;
   const size_t lds_bytes = (!samplewise && nbins <= kLdsBins) ? nbins * sizeof(int) : 0;
   auto s = stream();

@@ -1155,6 +1155,20 @@ def mc_topk_update(preds: Tensor, target: Tensor, ws: Tensor, flag: Tensor, k: i
     return True
 
 
+def mc_dense_update(preds: Tensor, target: Tensor, out: Tensor, flag: Tensor, num_classes: int,
+                    ignore_index: Optional[int], mode: int, samplewise: bool, top_k: int = 1) -> bool:
+    """:func:`mc_update` for ROCm float scores ``[N, C, ...]`` with a spatial axis (``X > 1``) on the channel-strided
+    kernels of ``csrc/classification/mc_dense.hip``; ``top_k > 1`` (``MC_STATS`` only) keeps the k best classes of a
+    pixel in registers.  Returns False (nothing done) when the kernels do not apply: CPU tensors, ``X == 1``, f64 /
+    integer preds, ``top_k`` outside ``[1, min(16, C)]``."""
+    if not (preds.is_cuda and preds.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            and 1 <= top_k <= _TOPK_MAX and not target.is_floating_point()):
+        return False
+    return _ops().mc_dense_update(preds.contiguous(), target.contiguous(), out, flag, int(num_classes),
+                                  0 if ignore_index is None else int(ignore_index), ignore_index is not None,
+                                  int(mode), samplewise, int(top_k))
+
+
 # -------------------------------------------------------------------------------------------- curve scores
 SCORE_AUROC, SCORE_AP = 0, 1
 _AVG_IDS = {None: 0, "none": 0, "macro": 1, "weighted": 2}
