@@ -1,10 +1,13 @@
 """Spatial / pansharpening quality: SCC, VIF, D_lambda, D_s, QNR.
 
 Behavioural references: ``F/image/scc.py``, ``vif.py``, ``d_lambda.py``, ``d_s.py``, ``qnr.py``.  Channel loops of
-the reference become grouped convolutions / batched planes; the band-pair UQI matrix of D_lambda is one batched call
+the reference become grouped convolutions / batched planes; on ROCm SCC is one launch and VIF one launch per scale of
+the window kernels, with the high-pass filter and the blur-and-decimate step between the scales fused into the
+kernels' LDS tiles (``csrc/image/window_prefilter.hip``); the band-pair UQI matrix of D_lambda is one batched call
 of the fused UQI kernel over all ``C(C-1)/2`` pairs; the ``pan`` degradation of D_s is an in-house box filter +
 bilinear resize (no torchvision dependency).
 """
+import functools
 import math
 from typing import Literal, Optional, Tuple, Union
 
@@ -15,7 +18,7 @@ from torch import Tensor
 from torchmetrics_amd import ops
 
 from torchmetrics_amd.functional.image.helper import _symmetric_pad, _uniform_filter
-from torchmetrics_amd.functional.image.ssim import _uqi_plane_means
+from torchmetrics_amd.functional.image.ssim import _uqi_plane_means, _wants_grad
 from torchmetrics_amd.utilities.checks import _check_same_shape
 from torchmetrics_amd.utilities.distributed import reduce
 
@@ -47,12 +50,28 @@ def _scc_update(preds: Tensor, target: Tensor, hp_filter: Tensor, window_size: i
 def _scc_plane_means(preds: Tensor, target: Tensor, hp_filter: Tensor, window_size: int) -> Tensor:
     """Per-image SCC averaged over channels and pixels, ``[B]``.
 
-    ROCm: after the (symmetric-padded) high-pass convolution, the zero-padded windowed moments and the per-window
-    correlation run in one launch of the SSIM window kernel (SCC mode, uniform separable window, per-tile sums); the
-    reference stacks 5 maps, runs a grouped conv and forms the map elementwise (``F/image/scc.py:41-90``)."""
+    ROCm (no gradient wanted, window up to 33, filter edges up to 9 and no larger than the image): one launch of the
+    fused SCC kernel (``ops.scc_partials``), which stages each tile with the symmetric border folded into its index
+    arithmetic, applies the high-pass filter into LDS, zeroes it outside the image and runs the uniform window
+    moments and the per-window correlation on that tile; no padded, filtered or re-packed copy of the images exists.
+    The reference pads, convolves, stacks 5 maps, runs a grouped conv and forms the map elementwise
+    (``F/image/scc.py:41-90``); everything else here takes that formulation (``_scc_map``)."""
     b, c, h, w = preds.shape
-    if not (preds.is_cuda and window_size <= 33):
-        return _scc_map(preds, target, hp_filter, window_size).mean(dim=[1, 2, 3])
+    kh, kw = hp_filter.shape[-2:]
+    if not ops.window_prefilter_enabled():
+        if preds.is_cuda and window_size <= 33:
+            return _scc_plane_means_conv(preds, target, hp_filter, window_size)
+    elif (preds.is_cuda and not _wants_grad(preds, target) and window_size <= ops.SCC_MAX_WINDOW
+          and kh <= min(ops.SCC_MAX_FILTER, h) and kw <= min(ops.SCC_MAX_FILTER, w)):
+        part = ops.scc_partials(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), hp_filter[0, 0], window_size)
+        return part.sum(1).reshape(b, c).sum(1) / (c * h * w)
+    return _scc_map(preds, target, hp_filter, window_size).mean(dim=[1, 2, 3])
+
+
+def _scc_plane_means_conv(preds: Tensor, target: Tensor, hp_filter: Tensor, window_size: int) -> Tensor:
+    """The ROCm path before the fused SCC kernel (``TM_AMD_WINDOW_PREFILTER=0``): vendor convolution for the high-pass
+    filter, padded and re-packed copies, then the SSIM window kernel in SCC mode."""
+    b, c, h, w = preds.shape
     x = torch.cat([preds, target], 0).reshape(2 * b * c, 1, h, w)
     kh, kw = hp_filter.shape[-2:]
     x = _symmetric_pad(x, 3, (kw - 1) // 2, math.ceil((kw - 1) / 2))
@@ -120,12 +139,18 @@ def _vif_filter(win_size: float, sigma: float, dtype: torch.dtype, device: torch
 def _vif_planes(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
     """Pixel-domain VIF of ``[P, 1, H, W]`` planes -> ``[P]``.
 
-    ROCm: each scale's windowed moments and the per-window VIF terms are one launch of the SSIM window kernel in its
-    VIF mode (separable Gaussian, valid windows, per-tile sums of numerator and denominator); only the 2x
-    downsampling between scales stays a strided convolution.  The reference stacks 5 maps, runs a grouped conv and
-    ~25 elementwise ops per scale (``F/image/vif.py:41-80``)."""
-    if preds.is_cuda and preds.dtype in (torch.float32, torch.float64):
-        return _vif_planes_fused(preds, target, sigma_n_sq)
+    ROCm (fp32 / fp64 / bf16 / fp16, no gradient wanted): four launches, one per scale (``_vif_planes_fused``).  Scale
+    0 is the SSIM window kernel in its VIF mode; each later scale is one launch of the fused pyramid kernel
+    (``ops.vif_scale``), which blurs and decimates the previous scale's planes inside its LDS tile, writes the
+    decimated planes for the next scale and sums the per-window VIF terms.  16-bit inputs are widened on load and
+    everything after that, the ``[P]`` ratios included, is fp32.  Inputs that want a gradient, and every other device
+    or dtype, take the torch composition below; the reference stacks 5 maps, runs a grouped conv and ~25 elementwise
+    ops per scale (``F/image/vif.py:41-80``)."""
+    if preds.is_cuda and ops.window_prefilter_enabled():
+        if preds.dtype in _VIF_FUSED_DTYPES and not _wants_grad(preds, target):
+            return _vif_planes_fused(preds, target, sigma_n_sq)
+    elif preds.is_cuda and preds.dtype in (torch.float32, torch.float64):
+        return _vif_planes_fused_conv(preds, target, sigma_n_sq)
     dtype, device = preds.dtype, preds.device
     eps = torch.tensor(1e-10, dtype=dtype, device=device)
     sn = torch.tensor(sigma_n_sq, dtype=dtype, device=device)
@@ -161,7 +186,33 @@ def _vif_planes(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
     return num / den
 
 
+_VIF_FUSED_DTYPES = (torch.float32, torch.float64, torch.bfloat16, torch.float16)
+
+
+@functools.lru_cache(maxsize=None)
+def _vif_taps(acc: torch.dtype, device: torch.device) -> Tuple[Tensor, ...]:
+    """The four scales' 1-D Gaussians on ``device``: the normalised 2-D filter of a scale is the outer product of its
+    1-D one with itself.  Computed once in fp64 on the host, so a call launches nothing for them."""
+    return tuple(_vif_filter(2.0 ** (4 - s) + 1, (2.0 ** (4 - s) + 1) / 5, torch.float64, torch.device("cpu")).sum(1)
+                 .to(device=device, dtype=acc) for s in range(4))
+
+
 def _vif_planes_fused(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
+    acc = torch.float64 if preds.dtype == torch.float64 else torch.float32
+    consts = torch.tensor([sigma_n_sq, 0.0, 1e-10], dtype=acc, device=preds.device)
+    taps = _vif_taps(acc, preds.device)
+    x, y = target[:, 0], preds[:, 0]  # x = reference, y = distorted
+    parts = [ops.ssim2d_partials(x, y, taps[0], taps[0], consts, ops.VIF_MODE)]
+    for scale in range(1, 4):
+        x, y, part = ops.vif_scale(x, y, taps[scale], consts)
+        parts.append(part)
+    sums = torch.cat(parts, 1).sum(1)  # [P, tiles of all scales, 2] -> (numerator, denominator)
+    return sums[:, 0] / sums[:, 1]
+
+
+def _vif_planes_fused_conv(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
+    """The ROCm path before the fused pyramid kernel (``TM_AMD_WINDOW_PREFILTER=0``): vendor convolution plus strided
+    slice between the scales, the SSIM window kernel in VIF mode at each."""
     dtype, device = preds.dtype, preds.device
     consts = torch.tensor([sigma_n_sq, 0.0, 1e-10], dtype=dtype, device=device)
     num = torch.zeros(preds.shape[0], dtype=dtype, device=device)
@@ -192,7 +243,7 @@ def visual_information_fidelity(preds: Tensor, target: Tensor, sigma_n_sq: float
     # plane order channel-major to match the reference's per-channel concatenation
     p = preds.transpose(0, 1).reshape(c * b, 1, h, w)
     t = target.transpose(0, 1).reshape(c * b, 1, h, w)
-    return _vif_planes(p, t, sigma_n_sq).mean()
+    return _vif_planes(p, t, sigma_n_sq).mean().to(preds.dtype)  # 16-bit ROCm inputs: the one rounding of the result
 
 
 # ------------------------------------------------------------------------------------------------------ D_lambda

@@ -1240,6 +1240,47 @@ def ssim2d_partials(x: Tensor, y: Tensor, wh: Tensor, ww: Tensor, c12: Tensor, m
     return _cpu.ssim2d_partials(x, y, wh, ww, c12, mode)
 
 
+def window_prefilter_enabled() -> bool:
+    """``TM_AMD_WINDOW_PREFILTER=0`` (read at call time) sends VIF and SCC back through the vendor-convolution
+    prefilters in front of :func:`ssim2d_partials`, for A/B timing against :func:`vif_scale` / :func:`scc_partials`."""
+    return os.environ.get("TM_AMD_WINDOW_PREFILTER", "1") != "0"
+
+
+VIF_SCALE_MAX_TAPS = 17  # kMaxTaps of csrc/image/window_prefilter.hip
+SCC_MAX_FILTER = 9  # kMaxFilt
+SCC_MAX_WINDOW = 33  # kMaxWin
+
+
+def vif_scale(x: Tensor, y: Tensor, taps: Tensor, c12: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """One step of the VIF pyramid in one launch (``csrc/image/window_prefilter.hip``, ROCm only).
+
+    ``x`` (reference) / ``y`` (distorted): ``[P, H, W]`` in fp32 / fp64 / fp16 / bf16; ``taps``: the scale's 1-D
+    Gaussian (odd, at most ``VIF_SCALE_MAX_TAPS``); ``c12``: ``(sigma_n^2, -, eps)``.  Both planes are blurred with the
+    separable Gaussian and every second valid pixel is kept; the VIF terms are summed over the ``n x n`` windows of the
+    result.  Returns ``(xd, yd, part)``: the decimated planes ``[P, ceil((H-n+1)/2), ceil((W-n+1)/2)]`` in the
+    accumulation dtype (fp64 for fp64 inputs, else fp32) and ``[P, T, 2]`` per-tile (numerator, denominator) sums.
+    """
+    if not x.is_cuda:
+        raise ValueError("vif_scale serves ROCm tensors; CPU tensors take the convolution formulation")
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+        x, y = x.float(), y.float()
+    taps, c12 = (t.to(device=x.device, dtype=acc).contiguous() for t in (taps, c12))
+    return _ops().vif_scale(x.contiguous(), y.contiguous(), taps, c12)
+
+
+def scc_partials(x: Tensor, y: Tensor, filt: Tensor, window: int) -> Tensor:
+    """Per-tile sums ``[P, T]`` of the spatial correlation map of ROCm fp32 ``[P, H, W]`` planes in one launch
+    (``csrc/image/window_prefilter.hip``, ROCm only): the ``[kh, kw]`` high-pass ``filt`` (edges at most
+    ``SCC_MAX_FILTER`` and no larger than the plane) is applied as a true convolution over the symmetric-padded
+    planes and doubled, and the correlation is taken over every ``window x window`` neighbourhood (at most
+    ``SCC_MAX_WINDOW``) of the zero-padded result."""
+    if not x.is_cuda:
+        raise ValueError("scc_partials serves ROCm tensors; CPU tensors take the convolution formulation")
+    filt = filt.to(device=x.device, dtype=torch.float32).contiguous()
+    return _ops().scc_partials(x.float().contiguous(), y.float().contiguous(), filt, int(window))
+
+
 SSIM_GRAD_MAX_WINDOW = 15  # kMaxK of csrc/image/ssim_grad.hip
 
 
