@@ -3,9 +3,10 @@
 Behavioural references: ``F/image/scc.py``, ``vif.py``, ``d_lambda.py``, ``d_s.py``, ``qnr.py``.  Channel loops of
 the reference become grouped convolutions / batched planes; on ROCm SCC is one launch and VIF one launch per scale of
 the window kernels, with the high-pass filter and the blur-and-decimate step between the scales fused into the
-kernels' LDS tiles (``csrc/image/window_prefilter.hip``); the band-pair UQI matrix of D_lambda is one batched call
-of the fused UQI kernel over all ``C(C-1)/2`` pairs; the ``pan`` degradation of D_s is an in-house box filter +
-bilinear resize (no torchvision dependency).
+kernels' LDS tiles (``csrc/image/window_prefilter.hip``); the band-pair UQI matrix of D_lambda is one launch of the
+band-pair kernel over all ``C(C-1)/2`` pairs and the ``pan`` degradation of D_s (box filter + bilinear resize) one
+launch of the pan kernel (``csrc/image/band_uqi.hip``); elsewhere the pairs are gathered into one batched UQI call and
+the degradation is an in-house torch composition (no torchvision dependency).
 """
 import functools
 import math
@@ -17,7 +18,7 @@ from torch import Tensor
 
 from torchmetrics_amd import ops
 
-from torchmetrics_amd.functional.image.helper import _symmetric_pad, _uniform_filter
+from torchmetrics_amd.functional.image.helper import _symmetric_pad, _uniform_filter, _window_1d
 from torchmetrics_amd.functional.image.ssim import _uqi_plane_means, _wants_grad
 from torchmetrics_amd.utilities.checks import _check_same_shape
 from torchmetrics_amd.utilities.distributed import reduce
@@ -264,9 +265,45 @@ def _spectral_distortion_index_update(preds: Tensor, target: Tensor) -> Tuple[Te
     return preds, target
 
 
+_BAND_UQI_DTYPES = (torch.float32, torch.float64, torch.bfloat16, torch.float16)
+
+
+@functools.lru_cache(maxsize=None)
+def _band_uqi_args(dtype: torch.dtype, device: torch.device) -> Tuple[Tensor, Tensor]:
+    """The 11-tap Gaussian (sigma 1.5) and ``(-, -, eps)`` of the band-pair kernel on ``device``, in its accumulation
+    dtype; ``eps`` is that of the input ``dtype``, as in ``_uqi_plane_means``.  Computed once on the host in fp64."""
+    acc = torch.float64 if dtype == torch.float64 else torch.float32
+    taps = _window_1d((11,), (1.5,), True, torch.float64, torch.device("cpu"))[0].to(device=device, dtype=acc)
+    return taps, torch.tensor([0.0, 0.0, torch.finfo(dtype).eps], dtype=torch.float64).to(device=device, dtype=acc)
+
+
+@functools.lru_cache(maxsize=None)
+def _triu_pairs(c: int, device: torch.device) -> Tuple[Tensor, Tensor]:
+    iu = torch.triu_indices(c, c, offset=1).to(device)
+    return iu[0], iu[1]
+
+
+def _no_grad_rocm(x: Tensor) -> bool:
+    """``x`` is served by the forward-only band-pair / pan kernels: on ROCm, no gradient wanted, switch not off."""
+    return (x.is_cuda and x.dtype in _BAND_UQI_DTYPES and not (x.requires_grad and torch.is_grad_enabled())
+            and ops.band_uqi_enabled())
+
+
 def _band_uqi_matrix(x: Tensor) -> Tensor:
-    """Symmetric ``[C, C]`` matrix of per-band-pair UQI (mean over the batch), all pairs in one batched call."""
+    """Symmetric ``[C, C]`` matrix of per-band-pair UQI (mean over the batch).
+
+    ROCm (no gradient wanted, at least two bands, image at least 11 x 11): one launch of the band-pair kernel
+    (``ops.band_uqi_partials``), which stages every band tile once per group pair and keeps the per-band window
+    statistics in registers; the matrix is in the accumulation dtype (fp32 for 16-bit inputs), so the metric is
+    rounded to the input dtype once.  Everything else gathers the pairs into one batched UQI call."""
     b, c = x.shape[:2]
+    if c >= 2 and x.ndim == 4 and min(x.shape[-2:]) >= 11 and _no_grad_rocm(x):
+        taps, consts = _band_uqi_args(x.dtype, x.device)
+        part = ops.band_uqi_partials(x, taps, consts)
+        per_pair = part.sum((0, 1)) / (b * (x.shape[-2] - 10) * (x.shape[-1] - 10))
+        m = torch.zeros(c, c, dtype=part.dtype, device=x.device)
+        m[_triu_pairs(c, x.device)] = per_pair
+        return m + m.T
     m = torch.zeros(c, c, dtype=x.dtype, device=x.device)
     if c < 2:
         return m
@@ -289,7 +326,8 @@ def _spectral_distortion_index_compute(
         out = torch.pow(diff, 1.0 / p)
     else:
         out = torch.pow(1.0 / (length * (length - 1)) * torch.sum(diff), 1.0 / p)
-    return reduce(out, reduction)
+    # 16-bit ROCm inputs: the band-pair kernel's matrices are fp32 and this is the one rounding of the result
+    return reduce(out, reduction).to(preds.dtype)
 
 
 def spectral_distortion_index(
@@ -351,7 +389,10 @@ def _spatial_distortion_index_compute(
         raise ValueError(
             f"Expected `window_size` to be smaller than dimension of `ms`. Got window_size: {window_size}."
         )
-    if pan_lr is None:
+    if pan_lr is None and window_size <= ops.PAN_DEGRADE_MAX_WINDOW and _no_grad_rocm(pan):
+        # one launch: the box filter evaluated only at the pixels the resize reads (csrc/image/band_uqi.hip)
+        pan_lr = ops.pan_degrade(pan, window_size, (ms_h, ms_w))
+    elif pan_lr is None:
         degraded = _uniform_filter(pan, window_size=window_size)
         pan_lr = F.interpolate(degraded, size=(ms_h, ms_w), mode="bilinear", align_corners=False, antialias=False)
     c = preds.shape[1]

@@ -1281,6 +1281,45 @@ def scc_partials(x: Tensor, y: Tensor, filt: Tensor, window: int) -> Tensor:
     return _ops().scc_partials(x.float().contiguous(), y.float().contiguous(), filt, int(window))
 
 
+def band_uqi_enabled() -> bool:
+    """``TM_AMD_BAND_UQI=0`` (read at call time) sends D_lambda / D_s / QNR back through the gathered band pairs in
+    front of :func:`ssim2d_partials` and the torch box filter + resize, for A/B timing against
+    :func:`band_uqi_partials` / :func:`pan_degrade`."""
+    return os.environ.get("TM_AMD_BAND_UQI", "1") != "0"
+
+
+BAND_UQI_MAX_WINDOW = 15  # kMaxK of csrc/image/band_uqi.hip
+PAN_DEGRADE_MAX_WINDOW = 33  # kMaxBox
+
+
+def band_uqi_partials(x: Tensor, taps: Tensor, consts: Tensor) -> Tensor:
+    """Per-tile sums ``[B, T, C(C-1)/2]`` of the UQI map of every band pair ``i < j`` of ``x`` ``[B, C, H, W]`` over the
+    windows fully inside the image, in one launch (``csrc/image/band_uqi.hip``, ROCm only).
+
+    ``x``: fp32 / fp64 / fp16 / bf16 with at least two bands; ``taps``: the 1-D window (odd, at most
+    ``BAND_UQI_MAX_WINDOW``, no larger than the image); ``consts``: ``(-, -, eps)``.  Pairs are in
+    ``triu_indices(C, C, 1)`` order; callers sum dim 1.  No atomics: two calls give identical bits."""
+    if not x.is_cuda:
+        raise ValueError("band_uqi_partials serves ROCm tensors; CPU tensors take the batched band-pair formulation")
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+        x = x.float()
+    taps, consts = (t.to(device=x.device, dtype=acc).contiguous() for t in (taps, consts))
+    return _ops().band_uqi_partials(x.contiguous(), taps, consts)
+
+
+def pan_degrade(pan: Tensor, window: int, size: Tuple[int, int]) -> Tensor:
+    """``F.interpolate(_uniform_filter(pan, window), size, mode="bilinear")`` of ``[B, C, H, W]`` planes in one launch
+    (``csrc/image/band_uqi.hip``, ROCm only) for sizes that divide the image: the box filter over the mirror-padded
+    plane is evaluated only where the resize reads it.  ``window`` at most ``PAN_DEGRADE_MAX_WINDOW`` and no larger
+    than the image; accumulated in fp32 (fp64 for fp64 inputs) and rounded once to the input dtype."""
+    if not pan.is_cuda:
+        raise ValueError("pan_degrade serves ROCm tensors; CPU tensors take the torch composition")
+    if pan.dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+        raise ValueError(f"pan_degrade serves floating-point tensors, got {pan.dtype}")
+    return _ops().pan_degrade(pan.contiguous(), int(window), int(size[0]), int(size[1]))
+
+
 SSIM_GRAD_MAX_WINDOW = 15  # kMaxK of csrc/image/ssim_grad.hip
 
 
